@@ -40,6 +40,8 @@ Besides the contract line it reports
 `--gpus N` without a torchrun environment re-executes itself under `python -m torch.distributed.run` with N ranks; a
 rank count that differs from --gpus, or fewer visible GPUs than ranks, is an error (never a silent 1-GPU run).
 --e2e prints a SECOND JSON line with all four (variant x score threshold) runs of config 5 in fresh processes.
+--dump-outputs DIR writes what the last timed step returned (rank 0) as .npy files under DIR, for output-by-output comparison
+of two builds on the same seeded inputs (at most 64 MB: the pooled features as a seeded sample of RoIs).
 --dry-run (CPU, gloo) exercises only the launcher / rank plumbing / all-gather and prints a line with "dry_run": true —
 used by tests/test_dist.py; it measures nothing.
 """
@@ -89,6 +91,33 @@ def algorithmic_bytes(feats, n_boxes):
     return inp + out + n_boxes * 5 * 4
 
 
+DUMP_POOLED_ROWS = 1024        # 1024 of the 4000 pooled RoIs: 51.4 MB of fp32 (all of them are 200 MB)
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(path, out):
+    """--dump-outputs: what one step returned to its caller (`step()`: pooled features, kept count, gathered detections and
+    counts), as float32 / float64 DIR/<name>.npy.  The pooled features are a fixed, seeded sample of RoIs (their indices in
+    pooled_sample_rows.npy).  The inputs are seeded too, so two builds can be compared file by file."""
+    import numpy as np
+
+    pooled, num, dets, counts = out
+    rows = torch.randperm(pooled.shape[0], generator=torch.Generator().manual_seed(0))[:DUMP_POOLED_ROWS].sort().values
+    arrays = {
+        "pooled_sample": pooled[rows.to(pooled.device)].float().cpu().numpy(),
+        "pooled_sample_rows": rows.numpy().astype(np.float64),
+        "num_kept": num.cpu().numpy().astype(np.float64),
+        "detections": dets.float().cpu().numpy(),
+        "detection_counts": counts.cpu().numpy().astype(np.float64),
+    }
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_MAX_BYTES, f"--dump-outputs: {total} bytes over the {DUMP_MAX_BYTES} byte budget"
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+    return {"dir": path, "bytes": total, "arrays": sorted(arrays)}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -124,10 +153,14 @@ def main():
                     "1-GPU box; the line says so in config.parallelism)")
     ap.add_argument("--graph", action="store_true", help="replay the per-rank chain from a captured hipGraph (measured: no gain "
                     "over eager sync-free launches on this stack, so off by default)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last one returned "
+                    "(rank 0) as DIR/<name>.npy: a seeded sample of the pooled RoIs, the kept count, the gathered detections and counts")
     args = ap.parse_args()
 
     if args.gpus < 1:
         sys.exit("bench.py: --gpus must be >= 1")
+    if args.steps < 1:
+        sys.exit("bench.py: --steps must be >= 1")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(self_launch(args.gpus))      # one process per GPU: re-execute under torch.distributed.run
     rank = int(os.environ.get("RANK", "0"))
@@ -314,6 +347,10 @@ def main():
             if int(stable.item()):
                 break
         sync()
+        # the pre-roll length depends on timing: skip ahead in the rotation so that the timed steps (and the input set of the
+        # last one, what --dump-outputs writes) do not — to where the usual single pre-roll pair leaves them.  Pre-roll steps
+        # come in pairs, so this skips 0 or 2 sets, never back onto the set of the step before.
+        counter["i"] += (2 - preroll) % N_SETS
         t0 = time.perf_counter()
         marks[0].record()
         for i in range(args.steps):
@@ -330,6 +367,8 @@ def main():
     gc.callbacks.append(gc_probe)
     elapsed, preroll, per_step_seq = contract_region()
     host_enqueue_ms = host["enqueue_ms"]
+    # read now: the runs below reuse the buffers of the last timed step
+    dumped = dump_outputs(args.dump_outputs, held["out"]) if args.dump_outputs and rank == 0 else None
     # the same K steps in the OTHER stream mode (reported next to `value`, never `value` itself)
     other_stream_ms, other_launch_ms = None, None
     if graph is None:
@@ -495,6 +534,8 @@ def main():
             "traffic_measured_on_shipped_sources": traffic_current,
         },
     }
+    if dumped is not None:
+        result["dumped_outputs"] = dumped
 
     parity_ok = True
     if rank == 0 and not args.no_cpu_baseline:      # also under N > 1: the line of every run carries its own baseline and parity check

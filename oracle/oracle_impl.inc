@@ -295,7 +295,9 @@ static REAL FN(dcn_bilinear)(const REAL* in, int H, int W, REAL h, REAL w) {
 /* ---- forward = deformable_im2col (:134-209) contracted with the weights per group
  * (:921-1151): out[b,oc,y,x] = bias[oc] + sum_{ic,i,j} W[oc,ic,i,j] * mask * bilinear(...).
  * The contraction is accumulated in double and rounded once (the reference uses a BLAS GEMM
- * whose summation order is unspecified; parity is judged at 1e-4). */
+ * whose summation order is unspecified; parity is judged at 1e-4).
+ * The columns of one output row of a group are sampled once and shared by the group's OC / groups
+ * output channels; every output still sums its (ic, i, j) terms in that order. */
 void FN(oracle_deform_conv2d)(const REAL* in, const REAL* weight, const REAL* offset, const REAL* mask,
                               const REAL* bias, REAL* out, int B, int C, int H, int W, int OC, int kh, int kw, int sh,
                               int sw, int ph, int pw, int dh, int dw, int groups, int ogroups, int use_mask) {
@@ -303,32 +305,44 @@ void FN(oracle_deform_conv2d)(const REAL* in, const REAL* weight, const REAL* of
   const int ow = (W + 2 * pw - (dw * (kw - 1) + 1)) / sw + 1;
   const int ICg = C / groups, OCg = OC / groups, cpog = C / ogroups, KK = kh * kw;
   const size_t plane = (size_t)oh * ow;
+  REAL* cols = (REAL*)malloc(sizeof(REAL) * (size_t)ICg * KK * (ow > 0 ? ow : 1));   /* [ICg * KK][ow] */
+  double* acc = (double*)malloc(sizeof(double) * (size_t)(ow > 0 ? ow : 1));
   for (int b = 0; b < B; ++b)
-    for (int oc = 0; oc < OC; ++oc) {
-      const int g = oc / OCg;
-      for (int y = 0; y < oh; ++y)
-        for (int x = 0; x < ow; ++x) {
-          double acc = 0;
-          for (int ic = 0; ic < ICg; ++ic) {
-            const int c = g * ICg + ic, og = c / cpog;
-            const REAL* ip = in + ((size_t)b * C + c) * H * W;
-            const REAL* op = offset + ((size_t)(b * ogroups + og) * 2 * KK) * plane;
-            const REAL* mp = mask + ((size_t)(b * ogroups + og) * KK) * plane;
-            for (int i = 0; i < kh; ++i)
-              for (int j = 0; j < kw; ++j) {
-                const int t = i * kw + j;
+    for (int g = 0; g < groups; ++g)
+      for (int y = 0; y < oh; ++y) {
+        for (int ic = 0; ic < ICg; ++ic) {
+          const int c = g * ICg + ic, og = c / cpog;
+          const REAL* ip = in + ((size_t)b * C + c) * H * W;
+          const REAL* op = offset + ((size_t)(b * ogroups + og) * 2 * KK) * plane;
+          const REAL* mp = mask + ((size_t)(b * ogroups + og) * KK) * plane;
+          for (int i = 0; i < kh; ++i)
+            for (int j = 0; j < kw; ++j) {
+              const int t = i * kw + j;
+              REAL* cp = cols + ((size_t)ic * KK + t) * ow;
+              for (int x = 0; x < ow; ++x) {
                 const REAL mval = use_mask ? mp[(size_t)t * plane + (size_t)y * ow + x] : (REAL)1;
                 const REAL off_h = op[(size_t)(2 * t) * plane + (size_t)y * ow + x];
                 const REAL off_w = op[(size_t)(2 * t + 1) * plane + (size_t)y * ow + x];
                 const REAL yy = (y * sh - ph) + i * dh + off_h;
                 const REAL xx = (x * sw - pw) + j * dw + off_w;
-                const REAL col = mval * FN(dcn_bilinear)(ip, H, W, yy, xx);
-                acc += (double)weight[((size_t)oc * ICg + ic) * KK + t] * (double)col;
+                cp[x] = mval * FN(dcn_bilinear)(ip, H, W, yy, xx);
               }
-          }
-          out[(((size_t)b * OC + oc) * oh + y) * ow + x] = (REAL)(acc + (double)bias[oc]);
+            }
         }
-    }
+        for (int oc = g * OCg; oc < (g + 1) * OCg; ++oc) {
+          const REAL* wp = weight + (size_t)oc * ICg * KK;
+          for (int x = 0; x < ow; ++x) acc[x] = 0;
+          for (size_t k = 0; k < (size_t)ICg * KK; ++k) {
+            const double wv = (double)wp[k];
+            const REAL* cp = cols + k * ow;
+            for (int x = 0; x < ow; ++x) acc[x] += wv * (double)cp[x];
+          }
+          REAL* orow = out + (((size_t)b * OC + oc) * oh + y) * ow;
+          for (int x = 0; x < ow; ++x) orow[x] = (REAL)(acc[x] + (double)bias[oc]);
+        }
+      }
+  free(cols);
+  free(acc);
 }
 
 /* ---- box_iou_rotated_utils.h:67-383 via cpu/box_iou_rotated_kernel.cpp:29-115 */

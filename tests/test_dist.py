@@ -111,6 +111,38 @@ def test_bench_dry_run_with_four_ranks():
     assert line["n_gpus"] == 4 and line["gather_ok"] is True and line["gathered_images"] == 16
 
 
+def test_bench_dump_outputs_are_float_arrays_within_the_budget(tmp_path):
+    """`bench.py --dump-outputs`: what a step returns (pooled features of a seeded RoI sample, kept count, gathered detections
+    and counts) as float32 / float64 .npy files, at most 64 MB in all, the same sample on every call."""
+    import numpy as np
+
+    import bench
+
+    pooled = torch.randn(bench.BATCH * bench.PROPOSALS, bench.CHANNELS, bench.POOL, bench.POOL)
+    dets, counts = sharding.split_payload(torch.rand(bench.BATCH, bench.MAX_DETS * sharding.DET_FIELDS + 1), bench.MAX_DETS)
+    out = (pooled, torch.tensor([123]), dets, counts)
+    info = bench.dump_outputs(str(tmp_path / "a"), out)
+    bench.dump_outputs(str(tmp_path / "b"), out)
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == sorted(n + ".npy" for n in info["arrays"]) and info["bytes"] <= 64 << 20
+    total = 0
+    for f in files:
+        a, b = np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, b), f
+        total += a.nbytes
+    assert total == info["bytes"]
+    rows = np.load(tmp_path / "a" / "pooled_sample_rows.npy").astype(np.int64)
+    assert np.array_equal(np.load(tmp_path / "a" / "pooled_sample.npy"), pooled.numpy()[rows])
+    assert np.array_equal(np.load(tmp_path / "a" / "detections.npy"), dets.numpy())
+    assert np.array_equal(np.load(tmp_path / "a" / "detection_counts.npy"), counts.numpy())
+    assert np.load(tmp_path / "a" / "num_kept.npy").tolist() == [123.0]
+
+
+def test_bench_refuses_zero_steps():
+    p = _bench("--steps", "0", "--dry-run")
+    assert p.returncode != 0 and "--steps" in p.stderr
+
+
 def _payload_worker(rank, world, port, ret):
     os.environ["MASTER_ADDR"] = "127.0.0.1"
     os.environ["MASTER_PORT"] = str(port)
