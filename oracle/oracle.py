@@ -200,6 +200,46 @@ def deform_conv2d(x, weight, offset, mask, bias, stride, pad, dil, groups, offse
     return out
 
 
+def deform_conv2d_backward(grad, x, weight, offset, mask, bias, stride, pad, dil, groups, offset_groups, use_mask,
+                           coord_f32=False):
+    """torchvision::_deform_conv2d_backward (cpu/deform_conv2d_kernel.cpp:1153-1226) -> (grad_input, grad_weight,
+    grad_offset, grad_mask, grad_bias).  Per image and weight group, the two GEMMs of the reference (backward_gradient_inputs
+    :1000-1048, `columns = W^T x grad_out`; backward_gradient_parameters :1050-1151, `grad_weight += grad_out x columns^T`)
+    run here as float64 matmuls and are rounded once to the tensors' type; the gathers and scatters around them
+    (deformable_im2col, col2im, col2im_coord) are the C restatement.  grad_mask is zero without a mask, all five are zero
+    for an empty batch (as the reference's host code returns them).  coord_f32: a float64 evaluation of an fp32 (or 16-bit)
+    problem rounds each sampling coordinate to float32 as the fp32 operation does; the coordinate weight is discontinuous
+    where a coordinate crosses an integer, so without it one in ~10^6 samples of randn offsets sees other rows."""
+    grad, x, weight, offset, bias = _c(grad), _c(x), _c(weight), _c(offset), _c(bias)
+    sfx, _ = _sfx(x)
+    dt = x.dtype
+    B, C, H, W = x.shape
+    OC, ICg, kh, kw = weight.shape
+    KK = kh * kw
+    OCg = OC // groups
+    oh, ow = grad.shape[2:]
+    mask = _c(mask) if use_mask else np.zeros(1, dtype=dt)
+    gin = np.zeros((B, C, H, W), dtype=dt)
+    goff = np.zeros(offset.shape, dtype=dt)
+    gmask = np.zeros((B, offset_groups * KK, oh, ow), dtype=dt)
+    gw = np.zeros((groups, OCg, ICg * KK), dtype=np.float64)
+    gbias = grad.astype(np.float64).sum(axis=(0, 2, 3)).astype(dt)
+    if B == 0:
+        return gin, gw.reshape(weight.shape).astype(dt), goff, gmask, gbias
+    geo = (C, H, W, kh, kw, stride[0], stride[1], pad[0], pad[1], dil[0], dil[1], offset_groups, int(use_mask), int(coord_f32))
+    w64 = weight.astype(np.float64).reshape(groups, OCg, ICg * KK)
+    cols = np.empty((C * KK, oh * ow), dtype=dt)
+    L = lib()
+    for b in range(B):
+        g64 = grad[b].astype(np.float64).reshape(groups, OCg, oh * ow)
+        cols[:] = np.matmul(w64.transpose(0, 2, 1), g64).reshape(C * KK, oh * ow)
+        getattr(L, f"oracle_deform_conv2d_backward_{sfx}")(_p(cols), _p(x), _p(offset), _p(mask), _p(gin), _p(goff),
+                                                           _p(gmask), b, *geo)
+        getattr(L, f"oracle_deform_conv2d_im2col_{sfx}")(_p(x), _p(offset), _p(mask), _p(cols), b, *geo)
+        gw += np.matmul(g64, cols.astype(np.float64).reshape(groups, ICg * KK, oh * ow).transpose(0, 2, 1))
+    return gin, gw.reshape(weight.shape).astype(dt), goff, gmask, gbias
+
+
 def box_iou_rotated(b1, b2):
     b1, b2 = _c(b1), _c(b2)
     sfx, _ = _sfx(b1)

@@ -465,3 +465,131 @@ void FN(oracle_box_iou_rotated)(const REAL* b1, const REAL* b2, float* out, int 
   for (int i = 0; i < N; ++i)
     for (int j = 0; j < M; ++j) out[(size_t)i * M + j] = (float)FN(rot_iou)(b1 + 5 * i, b2 + 5 * j);
 }
+
+/* A sampling coordinate of the backward, `(out_y * stride_h - pad_h) + i * dilation_h + offset_h` (:301-302, :525-526).
+ * coord_f32: round it to float as the reference's fp32 build does (scalar_t = float), for a double evaluation of an fp32
+ * problem — the coordinate weight jumps where the coordinate crosses an integer, so the rounding decides which rows it sees. */
+static REAL FN(dcn_coord)(int base, REAL off, int coord_f32) {
+  const REAL v = base + off;
+  return coord_f32 ? (REAL)(float)v : v;
+}
+
+/* ---- deformable_im2col (cpu/deform_conv2d_kernel.cpp:134-209) for image b: cols[(c * kh + i) * kw + j][y * ow + x] =
+ * mask * bilinear(...), the `columns` that backward_gradient_parameters (:1050-1151) contracts with grad_out. */
+void FN(oracle_deform_conv2d_im2col)(const REAL* in, const REAL* offset, const REAL* mask, REAL* cols, int b, int C, int H,
+                                     int W, int kh, int kw, int sh, int sw, int ph, int pw, int dh, int dw, int ogroups,
+                                     int use_mask, int coord_f32) {
+  const int oh = (H + 2 * ph - (dh * (kh - 1) + 1)) / sh + 1;
+  const int ow = (W + 2 * pw - (dw * (kw - 1) + 1)) / sw + 1;
+  const int KK = kh * kw, cpog = C / ogroups;
+  const size_t plane = (size_t)oh * ow;
+  for (int c = 0; c < C; ++c) {
+    const int og = c / cpog;
+    const REAL* ip = in + ((size_t)b * C + c) * H * W;
+    const REAL* op = offset + ((size_t)(b * ogroups + og) * 2 * KK) * plane;
+    const REAL* mp = mask + ((size_t)(b * ogroups + og) * KK) * plane;
+    for (int i = 0; i < kh; ++i)
+      for (int j = 0; j < kw; ++j) {
+        const int t = i * kw + j;
+        REAL* cp = cols + ((size_t)c * KK + t) * plane;
+        for (int y = 0; y < oh; ++y)
+          for (int x = 0; x < ow; ++x) {
+            const size_t pix = (size_t)y * ow + x;
+            const REAL mval = use_mask ? mp[(size_t)t * plane + pix] : (REAL)1;
+            const REAL yy = FN(dcn_coord)((y * sh - ph) + i * dh, op[(size_t)(2 * t) * plane + pix], coord_f32);
+            const REAL xx = FN(dcn_coord)((x * sw - pw) + j * dw, op[(size_t)(2 * t + 1) * plane + pix], coord_f32);
+            cp[pix] = mval * FN(dcn_bilinear)(ip, H, W, yy, xx);
+          }
+      }
+  }
+}
+
+/* ---- cpu/deform_conv2d_kernel.cpp:407-438 (get_coordinate_weight): the corner validity alone, NOT gated by the
+ * location test of bilinear_interpolate (a sample at y == -1 exactly still sees row 0). */
+static REAL FN(dcn_coordinate_weight)(const REAL* im, int H, int W, REAL y, REAL x, int is_y_direction) {
+  const int yl = (int)floor(y), xl = (int)floor(x);
+  const int yh = yl + 1, xh = xl + 1;
+  const int vyl = 0 <= yl && yl < H, vyh = 0 <= yh && yh < H;
+  const int vxl = 0 <= xl && xl < W, vxh = 0 <= xh && xh < W;
+  const REAL v_yx = (vyl && vxl) ? im[yl * W + xl] : (REAL)0;
+  const REAL v_yX = (vyl && vxh) ? im[yl * W + xh] : (REAL)0;
+  const REAL v_Yx = (vyh && vxl) ? im[yh * W + xl] : (REAL)0;
+  const REAL v_YX = (vyh && vxh) ? im[yh * W + xh] : (REAL)0;
+  if (is_y_direction) {
+    const REAL dx = x - xl;
+    return dx * (v_YX - v_yX) + (1 - dx) * (v_Yx - v_yx);
+  }
+  const REAL dy = y - yl;
+  return dy * (v_YX - v_Yx) + (1 - dy) * (v_yX - v_yx);
+}
+
+/* ---- the data gradients of image b from its `columns` (cols[(c * kh + i) * kw + j][y * ow + x] = W^T x grad_out per
+ * weight group, formed by the caller as backward_gradient_inputs does, :1000-1048):
+ *   grad_input  += deformable_col2im (:274-348): mask * (1 - |y - yp|) * (1 - |x - xp|) * column, for the corners
+ *                  yp in int(y) + {-1, 0, 1} with |y - yp| < 1 (the same gate as bilinear_interpolate);
+ *   grad_offset  = deformable_col2im_coord (:440-551): sum over the offset group's channels of mask * coordinate weight
+ *                  * column, component 2t = y, 2t + 1 = x;
+ *   grad_mask    = sum of column * bilinear(...) over the same channels (only with use_mask; the caller zeroes it).
+ * grad_input must be zeroed by the caller; grad_offset / grad_mask rows of image b are overwritten. */
+void FN(oracle_deform_conv2d_backward)(const REAL* cols, const REAL* in, const REAL* offset, const REAL* mask,
+                                       REAL* grad_in, REAL* grad_off, REAL* grad_mask, int b, int C, int H, int W, int kh,
+                                       int kw, int sh, int sw, int ph, int pw, int dh, int dw, int ogroups, int use_mask,
+                                       int coord_f32) {
+  const int oh = (H + 2 * ph - (dh * (kh - 1) + 1)) / sh + 1;
+  const int ow = (W + 2 * pw - (dw * (kw - 1) + 1)) / sw + 1;
+  const int KK = kh * kw, cpog = C / ogroups;
+  const size_t plane = (size_t)oh * ow;
+  /* col2im */
+  for (int c = 0; c < C; ++c) {
+    const int og = c / cpog;
+    const REAL* op = offset + ((size_t)(b * ogroups + og) * 2 * KK) * plane;
+    const REAL* mp = mask + ((size_t)(b * ogroups + og) * KK) * plane;
+    REAL* gp = grad_in + ((size_t)b * C + c) * H * W;
+    for (int i = 0; i < kh; ++i)
+      for (int j = 0; j < kw; ++j) {
+        const int t = i * kw + j;
+        const REAL* cp = cols + ((size_t)c * KK + t) * plane;
+        for (int oy = 0; oy < oh; ++oy)
+          for (int ox = 0; ox < ow; ++ox) {
+            const size_t pix = (size_t)oy * ow + ox;
+            const REAL mval = use_mask ? mp[(size_t)t * plane + pix] : (REAL)1;
+            const REAL y = FN(dcn_coord)((oy * sh - ph) + i * dh, op[(size_t)(2 * t) * plane + pix], coord_f32);
+            const REAL x = FN(dcn_coord)((ox * sw - pw) + j * dw, op[(size_t)(2 * t + 1) * plane + pix], coord_f32);
+            for (int ddy = -1; ddy <= 1; ++ddy)
+              for (int ddx = -1; ddx <= 1; ++ddx) {
+                const int yp = (int)y + ddy, xp = (int)x + ddx;
+                if (0 <= yp && yp < H && 0 <= xp && xp < W && fabs(y - yp) < 1 && fabs(x - xp) < 1) {
+                  const REAL wgt = (1 - (REAL)fabs(y - yp)) * (1 - (REAL)fabs(x - xp));
+                  gp[(size_t)yp * W + xp] += mval * wgt * cp[pix];
+                }
+              }
+          }
+      }
+  }
+  /* col2im_coord */
+  for (int og = 0; og < ogroups; ++og) {
+    const REAL* op = offset + ((size_t)(b * ogroups + og) * 2 * KK) * plane;
+    const REAL* mp = mask + ((size_t)(b * ogroups + og) * KK) * plane;
+    REAL* gop = grad_off + ((size_t)(b * ogroups + og) * 2 * KK) * plane;
+    REAL* gmp = grad_mask + ((size_t)(b * ogroups + og) * KK) * plane;
+    for (int oc = 0; oc < 2 * KK; ++oc) {
+      const int t = oc / 2, i = t / kw, j = t % kw, is_y = oc % 2 == 0;
+      for (int oy = 0; oy < oh; ++oy)
+        for (int ox = 0; ox < ow; ++ox) {
+          const size_t pix = (size_t)oy * ow + ox;
+          const REAL mval = use_mask ? mp[(size_t)t * plane + pix] : (REAL)1;
+          const REAL y = FN(dcn_coord)((oy * sh - ph) + i * dh, op[(size_t)(2 * t) * plane + pix], coord_f32);
+          const REAL x = FN(dcn_coord)((ox * sw - pw) + j * dw, op[(size_t)(2 * t + 1) * plane + pix], coord_f32);
+          REAL goff = 0, gm = 0;
+          for (int c = og * cpog; c < (og + 1) * cpog; ++c) {
+            const REAL* im = in + ((size_t)b * C + c) * H * W;
+            const REAL col = cols[((size_t)c * KK + t) * plane + pix];
+            goff += mval * FN(dcn_coordinate_weight)(im, H, W, y, x, is_y) * col;
+            if (use_mask && is_y) gm += col * FN(dcn_bilinear)(im, H, W, y, x);
+          }
+          gop[(size_t)oc * plane + pix] = goff;
+          if (use_mask && is_y) gmp[(size_t)t * plane + pix] = gm;
+        }
+    }
+  }
+}

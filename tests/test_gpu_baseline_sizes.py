@@ -249,9 +249,10 @@ BF16_BWD_BAR = {  # measured (round 6): g=1 3.14e-3 / 3.69e-3 / 2.27e-3 / 3.40e-
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16], ids=["fp32", "bf16"])
 def test_config4_deform_conv2d_backward_full_size(tv, groups, dtype):
     """`_deform_conv2d_backward` at config-4 size (2x256x100x136, k3, 256 -> 256, mask on) against the
-    reference CPU kernel (cpu/deform_conv2d_kernel.cpp:1153-1226) — all five gradients.  fp32: sums of up to 2304 (g=1) /
-    27,200 (weights: over the pixels) products in another order, bar 1e-4 relative to the gradient's own scale.  bf16: the
-    reference computes the 16-bit backward in the 16-bit type; ours is compared with the fp32 reference on the rounded
+    double-precision restatement of the reference CPU kernel (oracle.deform_conv2d_backward, cpu/deform_conv2d_kernel.cpp:
+    1153-1226; about 5 s per call) — all five gradients.  fp32: sums of up to 2304 (g=1) / 27,200 (weights: over the pixels)
+    products in another order, bar 1e-4 relative to the gradient's own scale.  bf16: the reference computes the 16-bit
+    backward in the 16-bit type; ours is compared with the oracle on the rounded
     tensors: the `columns` intermediate is a 16-bit tensor (in the reference too, cuda/deform_conv2d_kernel.cu:752-1033) and
     the result is rounded once more: the bar is absolute, per gradient, = the worst error measured + 20 % (BF16_BWD_BAR; round 5
     had one 3e-2 bar with an rtol of the same size on top)."""
@@ -263,21 +264,17 @@ def test_config4_deform_conv2d_backward_full_size(tv, groups, dtype):
     m = torch.rand(B, 9, H, W, generator=g).to(dtype)
     b = torch.randn(OC, generator=g).to(dtype)
     gr = torch.randn(B, OC, H, W, generator=g).to(dtype)
-    if not O.load_reference():
-        pytest.skip("needs the reference CPU kernels (oracle/_ref): the C restatement has no deform_conv2d backward")
     got = tv._deform_conv2d_backward(gr.to(DEV), x.to(DEV), w.to(DEV), off.to(DEV), m.to(DEV), b.to(DEV), 1, 1, 1, 1, 1, 1, groups, 1, True)
-    if True:
-        ref = torch.ops.torchvision._deform_conv2d_backward(gr.float(), x.float(), w.float(), off.float(), m.float(), b.float(),
-                                                            1, 1, 1, 1, 1, 1, groups, 1, True)
-        ref = [r.numpy() for r in ref]
+    ref = O.deform_conv2d_backward(*(v.double().numpy() for v in (gr, x, w, off, m, b)), (1, 1), (1, 1), (1, 1), groups, 1, True,
+                                   coord_f32=True)
     measured = {}
     for name, a, r in zip(("grad_input", "grad_weight", "grad_offset", "grad_mask", "grad_bias"), got, ref):
         assert a.dtype == dtype, name
         scale = max(1.0, float(np.abs(r).max()))
-        err = float(np.abs(a.float().cpu().numpy() - r).max()) / scale
+        err = float(np.abs(a.double().cpu().numpy() - r).max()) / scale
         measured[name] = err
         if dtype == torch.float32:
-            np.testing.assert_allclose(a.float().cpu().numpy(), r, rtol=1e-4, atol=1e-4 * scale, err_msg=f"{name} groups={groups}")
+            np.testing.assert_allclose(a.double().cpu().numpy(), r, rtol=1e-4, atol=1e-4 * scale, err_msg=f"{name} groups={groups}")
         else:
             # an absolute bar only (no rtol on top), per gradient = the worst error measured on the MI355X
             # (round 6, printed below with -s) + 20 %, in units of the gradient's largest magnitude

@@ -75,10 +75,12 @@ def test_nms_dtypes_and_edges(tv):
         tv.nms(torch.rand(3, 4, device=DEV), torch.rand(4, device=DEV), 0.5)
 
 
-def test_nms_against_reference_cpu_kernel(tv, need_ref):
+def test_nms_against_reference_cpu_kernel(tv, ref_loaded):
+    """Against the reference CPU kernel (oracle/_ref) when it is loaded, else against the C restatement."""
     for seed in range(4):
         b, s = adversarial_nms_inputs(2500, 0.7, gen(10 + seed), dup=(seed % 2 == 1))
-        assert torch.equal(tv.nms(b.to(DEV), s.to(DEV), 0.7).cpu(), tv.nms(b, s, 0.7))
+        want = tv.nms(b, s, 0.7) if ref_loaded else torch.from_numpy(O.nms(b.numpy(), s.numpy(), 0.7))
+        assert torch.equal(tv.nms(b.to(DEV), s.to(DEV), 0.7).cpu(), want)
 
 
 def test_nms_threshold_edge_is_exact_without_the_division(tv):
@@ -683,6 +685,63 @@ def _dcn_bwd_inputs(cfg, dtype, seed=31):
     return [v.to(dtype) for v in (gr, x, w, off, m, b)], args
 
 
+def _dcn_bwd_oracle(ts, args):
+    """oracle.deform_conv2d_backward in float64 on the tensors as the GPU received them (the rounded ones for 16-bit), with
+    the sampling coordinates rounded to float32 as the kernels (and the reference's fp32 build) form them."""
+    sh, sw, ph, pw, dh, dw, groups, og, use_mask = args
+    coord_f32 = ts[1].dtype != torch.float64   # the sampling coordinates of an fp32 / 16-bit problem are fp32 numbers
+    gr, x, w, off, m, b = (v.double().numpy() for v in ts)
+    return [torch.from_numpy(a) for a in O.deform_conv2d_backward(gr, x, w, off, m, b, (sh, sw), (ph, pw), (dh, dw), groups, og,
+                                                                  use_mask, coord_f32=coord_f32)]
+
+
+# route -> options (dcn.bwd_mfma, dcn.bwd_owner, dcn.bwd_window)
+_BWD_ROUTES = {"default": (1, 1, 1), "window": (1, 0, 1), "global_atomics": (1, 0, 0), "direct": (0, 1, 1)}
+
+
+def _bwd_data_kernel(cfg, route, dtype):
+    """The data-gradient kernel tvmi_deform_conv2d_backward launches for `cfg` on `route`: a mirror of bwd_plan's shape
+    rules (deform_conv2d_bwd.hip: bwd_dw_passes, bwd_mfma_shape, bwd_own_shape, the LDS sizes of win_geom / own_geom)."""
+    mfma_on, owner_on, window_on = _BWD_ROUTES[route]
+    C, OC, groups, og = cfg["C"], cfg["OC"], cfg["groups"], cfg["og"]
+    ICg, OCg, cpog = C // groups, OC // groups, C // og
+    (kh, kw), (sh, sw), (dh, dw) = cfg["k"], cfg["stride"], cfg["dil"]
+    if dtype == torch.float64:
+        return "dcn_bwd_data_direct"
+    if owner_on and ICg == 1 and OCg == 1 and C == OC and cpog % 64 == 0 and cpog // 64 in (1, 2, 4):
+        return "dcn_bwd_dw_cl"
+    if not (mfma_on and OCg >= 16 and ICg >= 16 and (og == 1 or (cpog % 32 == 0 and ICg % 32 == 0))):
+        return "dcn_bwd_data_direct"
+    wsz = (7 * sh + (kh - 1) * dh + 8) * (15 * sw + (kw - 1) * dw + 8)   # 8 x 16 pixel tiles, halo 3 (+1 each side)
+    own_lds = (16 * (128 + 32) + 16 * (5 * 64 + 32) + 8 * 32 * 16 + (wsz + 1) * 64) * 4
+    if owner_on and kh == 3 and kw == 3 and ICg % 64 == 0 and own_lds <= 160 * 1024:
+        return "dcn_bwd_data_own"
+    if window_on and (2 * 16 * (64 + 128) + 64 * wsz) * 4 <= 160 * 1024:
+        return "dcn_bwd_data_mfma_win"
+    return "dcn_bwd_data_mfma<"
+
+
+def _dcn_bwd_on_route(tv, ts, args, route, kernel):
+    """One `_deform_conv2d_backward` on `route`, recorded by torch.profiler: the route's data-gradient kernel must be among
+    the launched kernels (a shape change that moves a case to another route fails here instead of passing unnoticed)."""
+    from torch.profiler import ProfilerActivity, profile
+
+    for name, v in zip(("dcn.bwd_mfma", "dcn.bwd_owner", "dcn.bwd_window"), _BWD_ROUTES[route]):
+        torch.ops.tvmi.set_option(name, v)
+    try:
+        dev = [v.to(DEV) for v in ts]
+        torch.cuda.synchronize()
+        with profile(activities=[ProfilerActivity.CUDA]) as prof:
+            got = tv._deform_conv2d_backward(*dev, *args)
+            torch.cuda.synchronize()
+    finally:
+        for name in ("dcn.bwd_mfma", "dcn.bwd_owner", "dcn.bwd_window"):
+            torch.ops.tvmi.set_option(name, 1)
+    names = {e.name for e in prof.events()}
+    assert any(kernel in n for n in names), (route, kernel, sorted(n for n in names if "dcn" in n))
+    return got
+
+
 def _dcn_bwd_compare(got, ref, tol, what):
     for name, a, r in zip(("grad_input", "grad_weight", "grad_offset", "grad_mask", "grad_bias"), got, ref):
         r = r.double().numpy()
@@ -694,40 +753,127 @@ def _dcn_bwd_compare(got, ref, tol, what):
 @pytest.mark.parametrize("cfg", DCN_BWD_CFGS, ids=[str(i) for i in range(len(DCN_BWD_CFGS))])
 def test_deform_conv2d_backward_fused_vs_reference(tv, cfg, route):
     """`_deform_conv2d_backward` = ONE call of tvmi_deform_conv2d_backward (deform_conv2d_bwd.hip: two fused matrix-core kernels
-    or the direct kernels; no `columns`, no library GEMM) against the reference CPU kernels
-    (cpu/deform_conv2d_kernel.cpp:274-348, 407-551, 1153-1226), all five gradients, on every route: offset groups, weight
-    groups, strides / dilations, channel and pixel tails, no mask, and zero offsets with padding (sampling rows at exactly
-    y = -1, where get_coordinate_weight still sees the row below while the bilinear sample is zero).  fp32 bar 1e-4 of the
-    gradient's scale (sums in another order)."""
-    if not O.load_reference():
-        pytest.skip("needs the reference CPU kernels (oracle/_ref)")
+    or the direct kernels; no `columns`, no library GEMM) against the double-precision restatement of the reference
+    (oracle.deform_conv2d_backward: cpu/deform_conv2d_kernel.cpp:274-348, 407-551, 1153-1226), all five gradients, on every
+    route: offset groups, weight groups, strides / dilations, channel and pixel tails, no mask, and zero offsets with padding
+    (sampling rows at exactly y = -1, where get_coordinate_weight still sees the row below while the bilinear sample is
+    zero).  fp32 bar 1e-4 of the gradient's scale (sums in another order).  The route's data-gradient kernel must run.
+    (default: the owner form where the shape allows it (3 x 3, 64-channel chunks), else the window kernel.)"""
     ts, args = _dcn_bwd_inputs(cfg, torch.float32)
-    # default: the owner form of the data-gradient kernel where the shape allows (3 x 3, 64-channel chunks), else the window kernel
-    torch.ops.tvmi.set_option("dcn.bwd_mfma", 0 if route == "direct" else 1)
-    torch.ops.tvmi.set_option("dcn.bwd_owner", 0 if route in ("window", "global_atomics") else 1)
-    torch.ops.tvmi.set_option("dcn.bwd_window", 0 if route == "global_atomics" else 1)
-    try:
-        got = tv._deform_conv2d_backward(*[v.to(DEV) for v in ts], *args)
-    finally:
-        torch.ops.tvmi.set_option("dcn.bwd_mfma", 1)
-        torch.ops.tvmi.set_option("dcn.bwd_owner", 1)
-        torch.ops.tvmi.set_option("dcn.bwd_window", 1)
-    _dcn_bwd_compare(got, tv._deform_conv2d_backward(*ts, *args), TOL, route)
+    got = _dcn_bwd_on_route(tv, ts, args, route, _bwd_data_kernel(cfg, route, torch.float32))
+    _dcn_bwd_compare(got, _dcn_bwd_oracle(ts, args), TOL, route)
 
 
 @pytest.mark.parametrize("dtype,tol,idx", [(torch.bfloat16, 1.5e-2, 0), (torch.float16, 2e-3, 1), (torch.bfloat16, 1.5e-2, 6), (torch.float64, 1e-10, 7),
                                            (torch.float64, 1e-10, 0)], ids=["bf16-mfma", "fp16-mfma", "bf16-direct", "fp64-direct", "fp64-large"])
 def test_deform_conv2d_backward_fused_other_dtypes(tv, dtype, tol, idx):
     """16-bit tensors are read natively, contracted and summed in fp32 and rounded once (the reference keeps `columns` and its
-    atomics in the 16-bit type): compared with the fp32 reference on the rounded tensors, bar = a few 16-bit ulps of the
-    gradient's scale.  fp64 always takes the direct kernels: 1e-10."""
-    if not O.load_reference():
-        pytest.skip("needs the reference CPU kernels (oracle/_ref)")
-    ts, args = _dcn_bwd_inputs(DCN_BWD_CFGS[idx], dtype)
-    got = tv._deform_conv2d_backward(*[v.to(DEV) for v in ts], *args)
+    atomics in the 16-bit type): compared with the double-precision oracle on the rounded tensors, bar = a few 16-bit ulps
+    of the gradient's scale.  fp64 always takes the direct kernels: 1e-10."""
+    cfg = DCN_BWD_CFGS[idx]
+    ts, args = _dcn_bwd_inputs(cfg, dtype)
+    got = _dcn_bwd_on_route(tv, ts, args, "default", _bwd_data_kernel(cfg, "default", dtype))
     assert all(a.dtype == dtype for a in got)
-    up = torch.float64 if dtype == torch.float64 else torch.float32
-    _dcn_bwd_compare(got, tv._deform_conv2d_backward(*[v.to(up) for v in ts], *args), tol, str(dtype))
+    _dcn_bwd_compare(got, _dcn_bwd_oracle(ts, args), tol, str(dtype))
+
+
+@pytest.mark.parametrize("dtype,tol", [(torch.bfloat16, 1.5e-2), (torch.float16, 2e-3)], ids=["bf16", "fp16"])
+@pytest.mark.parametrize("idx,route,kernel", [(9, "window", "dcn_bwd_data_mfma_win"), (10, "global_atomics", "dcn_bwd_data_mfma<"),
+                                              (11, "default", "dcn_bwd_data_own"), (12, "default", "dcn_bwd_data_own"),
+                                              (13, "default", "dcn_bwd_dw_cl"), (14, "default", "dcn_bwd_dw_cl"),
+                                              (6, "default", "dcn_bwd_data_direct")],
+                         ids=["window-9", "global-10", "owner-11", "owner-12", "dwcl-13", "dwcl-14", "direct-6"])
+def test_deform_conv2d_backward_16bit_every_route(tv, idx, route, kernel, dtype, tol):
+    """fp16 / bf16 on every data-gradient form (window, global atomics, owner, depthwise channels-last, direct) against the
+    double-precision oracle on the rounded tensors, at the 16-bit bars of test_deform_conv2d_backward_fused_other_dtypes."""
+    cfg = DCN_BWD_CFGS[idx]
+    ts, args = _dcn_bwd_inputs(cfg, dtype)
+    assert _bwd_data_kernel(cfg, route, dtype) == kernel
+    got = _dcn_bwd_on_route(tv, ts, args, route, kernel)
+    assert all(a.dtype == dtype for a in got)
+    _dcn_bwd_compare(got, _dcn_bwd_oracle(ts, args), tol, f"{dtype} {route}")
+
+
+# shapes for the edge inputs: the owner form needs whole 64-channel chunks of ICg; the window form takes an ICg tail (48)
+DCN_EDGE_CFGS = {
+    "owner": dict(B=2, C=64, OC=40, H=10, W=12, k=(3, 3), groups=1, og=1, stride=(1, 1), pad=(1, 1), dil=(1, 1), mask=True),
+    "window": dict(B=2, C=48, OC=40, H=9, W=13, k=(3, 3), groups=1, og=1, stride=(1, 1), pad=(1, 1), dil=(1, 1), mask=True),
+}
+
+
+def _dcn_edge_inputs(cfg, dtype, g):
+    """Sampling points where these kernels go wrong: exact integer coordinates (many taps share one corner, dy = 0 / dx = 0),
+    y = H - 1, y in (H - 1, H), y = H, x = W - 1, x = W, y = -1, offsets of +-1e4 (`far`), generic points; negative and
+    zero mask values.  All values are exact in bf16 / fp16."""
+    B, C, OC, H, W = cfg["B"], cfg["C"], cfg["OC"], cfg["H"], cfg["W"]
+    kh, kw = cfg["k"]
+    KK = kh * kw
+    oh, ow = H, W   # stride 1, pad 1, 3 x 3
+    i, j = torch.arange(KK) // kw, torch.arange(KK) % kw
+    base_y = ((torch.arange(oh) - 1)[:, None] + i[:, None, None]).float().expand(B, KK, oh, ow)
+    base_x = ((torch.arange(ow) - 1) + j[:, None, None]).float().expand(B, KK, oh, ow)
+
+    def targets(n):
+        kind = torch.randint(0, 8, (B, KK, oh, ow), generator=g)
+        rnd_int = torch.randint(0, n, (B, KK, oh, ow), generator=g).float()
+        frac = torch.randint(1, 8, (B, KK, oh, ow), generator=g).float() / 8
+        choices = [rnd_int, torch.full_like(frac, n - 1), n - 1 + frac, torch.full_like(frac, n), torch.full_like(frac, -1.0),
+                   rnd_int + frac - 1, rnd_int, rnd_int + frac]
+        return torch.stack(choices).gather(0, kind[None])[0]
+
+    off = torch.stack([targets(H) - base_y, targets(W) - base_x], 2)                    # [B, KK, 2, oh, ow]
+    far = torch.rand(B, KK, oh, ow, generator=g) < 0.1
+    sign = torch.where(torch.rand(B, KK, oh, ow, generator=g) < 0.5, -1.0, 1.0)
+    off = torch.where(far[:, :, None], (sign * 1e4)[:, :, None].expand_as(off), off).reshape(B, 2 * KK, oh, ow)
+    m = (torch.randint(-8, 9, (B, KK, oh, ow), generator=g).float() / 8)              # negative, zero and positive
+    x = torch.randn(B, C, H, W, generator=g)
+    w = torch.randn(OC, C, kh, kw, generator=g) * 0.1
+    b = torch.randn(OC, generator=g)
+    gr = torch.randn(B, OC, oh, ow, generator=g)
+    args = (*cfg["stride"], *cfg["pad"], *cfg["dil"], cfg["groups"], cfg["og"], cfg["mask"])
+    return [v.to(dtype) for v in (gr, x, w, off, m, b)], args, far
+
+
+@pytest.mark.parametrize("dtype,tol", [(torch.float32, TOL), (torch.bfloat16, 1.5e-2)], ids=["fp32", "bf16"])
+@pytest.mark.parametrize("shape,route", [("owner", "default"), ("owner", "direct"), ("window", "window"), ("window", "global_atomics")])
+def test_deform_conv2d_backward_edge_inputs(tv, shape, route, dtype, tol):
+    """Integer and boundary sampling coordinates, far offsets, negative / zero mask values and OC (40) / ICg (48) tails, against
+    the double-precision oracle.  Samples at offsets of +-1e4 contribute nothing: their grad_offset / grad_mask entries are
+    exactly zero, and a problem whose every sample is that far has exactly zero grad_input / grad_weight / grad_offset /
+    grad_mask."""
+    cfg = DCN_EDGE_CFGS[shape]
+    ts, args, far = _dcn_edge_inputs(cfg, dtype, gen(77))
+    kernel = _bwd_data_kernel(cfg, route, dtype)
+    got = _dcn_bwd_on_route(tv, ts, args, route, kernel)
+    _dcn_bwd_compare(got, _dcn_bwd_oracle(ts, args), tol, f"{shape} {route} {dtype}")
+    gi, gw, goff, gmask, gb = (a.cpu() for a in got)
+    B, KK, oh, ow = far.shape
+    assert torch.all(goff.reshape(B, KK, 2, oh, ow)[far[:, :, None].expand(B, KK, 2, oh, ow)] == 0)
+    assert torch.all(gmask[far] == 0)
+    gr, x, w, off, m, b = ts
+    off_far = torch.where(off.float() < 0, -1e4, 1e4).to(dtype)     # every sample far away
+    gi, gw, goff, gmask, gb = _dcn_bwd_on_route(tv, [gr, x, w, off_far, m, b], args, route, kernel)
+    for nm, a in (("grad_input", gi), ("grad_weight", gw), ("grad_offset", goff), ("grad_mask", gmask)):
+        assert int(torch.count_nonzero(a)) == 0, nm
+    np.testing.assert_allclose(gb.double().cpu().numpy(), gr.double().sum((0, 2, 3)).numpy(), rtol=tol, atol=tol)
+
+
+def test_deform_conv2d_backward_through_autograd_with_a_stride0_grad(tv):
+    """`y.sum().backward()` hands the backward an expanded grad_output (every stride 0) on the owner route: the five gradients
+    against the double-precision oracle with a grad of ones."""
+    cfg = DCN_EDGE_CFGS["owner"]
+    ts, args, _ = _dcn_edge_inputs(cfg, torch.float32, gen(78))
+    _, x, w, off, m, b = ts
+    leaves = [v.to(DEV).requires_grad_(True) for v in (x, w, off, m, b)]
+    from torch.profiler import ProfilerActivity, profile
+
+    with profile(activities=[ProfilerActivity.CUDA]) as prof:
+        y = vision_amd.deform_conv2d(leaves[0], leaves[2], leaves[1], leaves[4], cfg["stride"], cfg["pad"], cfg["dil"], leaves[3])
+        y.sum().backward()
+        torch.cuda.synchronize()
+    assert any("dcn_bwd_data_own" in e.name for e in prof.events())
+    ref = _dcn_bwd_oracle([torch.ones(y.shape), x, w, off, m, b], args)
+    _dcn_bwd_compare([leaves[i].grad for i in (0, 1, 2, 3, 4)], ref, TOL, "autograd")
 
 
 def test_deform_conv2d_backward_through_the_c_abi():
@@ -735,8 +881,6 @@ def test_deform_conv2d_backward_through_the_c_abi():
     workspace query sizes the call, a short workspace is refused."""
     import ctypes
 
-    if not O.load_reference():
-        pytest.skip("needs the reference CPU kernels (oracle/_ref)")
     lib = vision_amd._loader.kernels()
     cfg = DCN_BWD_CFGS[1]
     ts, args = _dcn_bwd_inputs(cfg, torch.float32)
@@ -759,7 +903,7 @@ def test_deform_conv2d_backward_through_the_c_abi():
     stream = torch.cuda.current_stream().cuda_stream
     assert lib.tvmi_deform_conv2d_backward(*ptrs, 0, *dims, 1, ws.data_ptr(), nbytes, stream) == 0
     torch.cuda.synchronize()
-    _dcn_bwd_compare(outs, torch.ops.torchvision._deform_conv2d_backward(*ts, *args), TOL, "ctypes")
+    _dcn_bwd_compare(outs, _dcn_bwd_oracle(ts, args), TOL, "ctypes")
     assert lib.tvmi_deform_conv2d_backward(*ptrs, 0, *dims, 1, ws.data_ptr(), nbytes - 1, stream) != 0
 
 
