@@ -590,6 +590,22 @@ int tvmi_normalize_resize_batch(const void* const* images, const int64_t* height
 int tvmi_paste_masks(const void* masks, const float* boxes, void* output, tvmi_dtype dt, int64_t N, int64_t M,
                      int64_t im_h, int64_t im_w, int64_t padding, void* stream);
 
+/* ------------------------------------------------------------- keypoint decoding --------
+ * Batched replacement of heatmaps_to_keypoints (models/detection/roi_heads.py, keypointrcnn_inference): for every
+ * detection r and keypoint k, the bicubic (align_corners=False) resize of maps[r, k] to the box's ceil size, its first
+ * argmax, and the keypoint at that pixel's centre.  The reference loops over detections in Python with two host syncs
+ * each; this is three launches for the whole batch, sync-free (the box sizes never reach the host).
+ *   maps [R,K,H,W] (dt: F32 / F16 / BF16, contiguous), rois [R,4] float32 xyxy;
+ *   xy [R,3,K] float32: x, y, 1 (the reference returns its [R,K,3] permuted view), scores [R,K] float32: the resized
+ *   value at the argmax, rounded to dt.  Upsampled values are bit-identical to tvmi_upsample_bicubic2d's per-output
+ *   kernel; argmax ties go to the lowest flat index, NaN beats everything (torch's rules); results are reproducible.
+ *   workspace: 256-byte aligned device scratch of at least tvmi_heatmaps_to_keypoints_workspace_bytes(R, K) bytes.
+ * Limits: K >= 1, H, W >= 1, H*W < 2^31, R*K < 2^31.  A box whose resized map exceeds 2^31 - 1 pixels, or with a
+ * non-finite coordinate, gets NaN x, y and score (the reference raises); R == 0 launches nothing. */
+size_t tvmi_heatmaps_to_keypoints_workspace_bytes(int64_t R, int64_t K);
+int tvmi_heatmaps_to_keypoints(const void* maps, const float* rois, float* xy, float* scores, tvmi_dtype dt, int64_t R,
+                               int64_t K, int64_t H, int64_t W, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ------------------------------------------------------------------ quantized ------
  * torchvision::qroi_align (quantized/cpu/qroi_align_kernel.cpp:22-178, CPU-only in the reference): `input` [1, C, H, W] and
  * `rois` [K, 5] are integer tensors of type `dt` with explicit (scale, zero point); bilinear sums on the raw integers,

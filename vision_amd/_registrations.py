@@ -190,6 +190,12 @@ def _fake_paste_masks(masks, boxes, im_h, im_w, padding):
     return masks.new_empty((masks.shape[0], 1, im_h, im_w))
 
 
+def _fake_heatmaps_to_keypoints(maps, rois):
+    R, K = maps.shape[0], maps.shape[1]
+    xy = maps.new_empty((R, 3, K), dtype=torch.float32).permute(0, 2, 1)
+    return xy, maps.new_empty((R, K), dtype=torch.float32)
+
+
 def _fake_detection_candidates(class_logits, box_regression, proposals, row_image, image_hw, weights, clip, score_thresh, min_size):
     R, C = class_logits.shape
     f = class_logits.new_empty
@@ -275,6 +281,7 @@ _FAKES = {
     "tvmi::pack_detections_payload": _fake_pack_payload,
     "tvmi::pack_detections_devcount": _fake_pack_devcount,
     "tvmi::paste_masks": _fake_paste_masks,
+    "tvmi::heatmaps_to_keypoints": _fake_heatmaps_to_keypoints,
     "tvmi::detection_candidates": _fake_detection_candidates,
     "tvmi::rpn_candidates": _fake_rpn_candidates,
     "tvmi::pack_detections": _fake_pack_detections,

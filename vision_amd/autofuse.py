@@ -6,6 +6,8 @@ the detectors their time —
 
     torchvision.ops.poolers.MultiScaleRoIAlign.forward                       (ops/poolers.py:289-321, loop :199-222)
     torchvision.models.detection.roi_heads.RoIHeads.postprocess_detections   (roi_heads.py:680-737)
+    torchvision.models.detection.roi_heads.keypointrcnn_inference            (the module global RoIHeads.forward calls:
+        heatmaps_to_keypoints' per-detection loop with two host syncs each)
     torchvision.models.detection.rpn.RegionProposalNetwork.filter_proposals  (rpn.py:242-297)
     torchvision.models.detection.retinanet.RetinaNet.postprocess_detections  (retinanet.py:509-571)
     torchvision.models.detection.transform.GeneralizedRCNNTransform.forward / .postprocess (transform.py:119-276)
@@ -35,13 +37,14 @@ _ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 _TARGETS = {
     "torchvision.ops.roi_align": [(None, "_roi_align", "make_deterministic_roi_align")],
     "torchvision.ops.poolers": [("MultiScaleRoIAlign", "forward", "make_pool_forward")],
-    "torchvision.models.detection.roi_heads": [("RoIHeads", "postprocess_detections", "make_postprocess_detections")],
+    "torchvision.models.detection.roi_heads": [("RoIHeads", "postprocess_detections", "make_postprocess_detections"),
+                                               (None, "keypointrcnn_inference", "make_keypointrcnn_inference")],
     "torchvision.models.detection.rpn": [("RegionProposalNetwork", "filter_proposals", "make_filter_proposals")],
     "torchvision.models.detection.retinanet": [("RetinaNet", "postprocess_detections", "make_retinanet_postprocess")],
     "torchvision.models.detection.transform": [("GeneralizedRCNNTransform", "forward", "make_transform_forward"),
                                                ("GeneralizedRCNNTransform", "postprocess", "make_transform_postprocess")],
 }
-_patched = []          # (class, method name, original) for uninstall()
+_patched = []          # (class or module, attribute name, original) for uninstall()
 _state = {"finder": None}
 
 

@@ -20,6 +20,7 @@
 #include <algorithm>
 #include <cmath>
 
+#include "resample_common.h"
 #include "tvmi_common.h"
 
 namespace tvmi {
@@ -27,22 +28,6 @@ namespace {
 
 constexpr int kThreads = 256;
 enum { MODE_BILINEAR = 0, MODE_BICUBIC = 1 };
-
-// UpSample.h:259-287
-__device__ __host__ inline float compute_scale(int64_t in, int64_t out, bool align, double scale_arg) {
-  if (align) return out > 1 ? (float)(in - 1) / (float)(out - 1) : 0.f;
-  return scale_arg > 0. ? (float)(1.0 / scale_arg) : (float)in / (float)out;
-}
-
-// UpSample.h:289-318
-__device__ __forceinline__ float source_index(float scale, int dst, bool align, bool cubic) {
-  if (align) return scale * (float)dst;
-  const float s = scale * ((float)dst + 0.5f) - 0.5f;
-  return (!cubic && s < 0.f) ? 0.f : s;
-}
-
-__device__ __forceinline__ float cubic1(float x, float A) { return ((A + 2) * x - (A + 3)) * x * x + 1; }
-__device__ __forceinline__ float cubic2(float x, float A) { return ((A * x - 5 * A) * x + 8 * A) * x - 4 * A; }
 
 struct Lin {
   int i0, i1;

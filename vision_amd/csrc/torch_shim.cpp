@@ -1133,6 +1133,31 @@ at::Tensor paste_masks(const at::Tensor& masks, const at::Tensor& boxes, int64_t
   return out;
 }
 
+// ---- batched heatmaps_to_keypoints (roi_heads.py, keypointrcnn_inference) in three launches, no host sync
+std::tuple<at::Tensor, at::Tensor> heatmaps_to_keypoints(const at::Tensor& maps, const at::Tensor& rois) {
+  TORCH_CHECK(maps.is_cuda() && rois.is_cuda(), "heatmaps_to_keypoints: CUDA tensors expected");
+  TORCH_CHECK(maps.dim() == 4 && maps.size(1) >= 1 && maps.size(2) >= 1 && maps.size(3) >= 1,
+              "heatmaps_to_keypoints: maps must have shape [R, K, H, W] with K, H, W >= 1");
+  TORCH_CHECK(rois.dim() == 2 && rois.size(1) == 4 && rois.size(0) == maps.size(0),
+              "heatmaps_to_keypoints: rois must have shape [R, 4]");
+  TORCH_CHECK(maps.scalar_type() == at::kFloat || maps.scalar_type() == at::kHalf || maps.scalar_type() == at::kBFloat16,
+              "heatmaps_to_keypoints: maps must be float32, float16 or bfloat16");
+  c10::DeviceGuard guard(maps.device());
+  const int64_t R = maps.size(0), K = maps.size(1), H = maps.size(2), W = maps.size(3);
+  const auto fopt = maps.options().dtype(at::kFloat);
+  at::Tensor xy = at::empty({R, 3, K}, fopt);
+  at::Tensor scores = at::empty({R, K}, fopt);
+  if (R == 0) return std::make_tuple(xy.permute({0, 2, 1}), scores);
+  at::Tensor m = maps.contiguous(), r = rois.to(at::kFloat).contiguous();
+  const size_t wb = tvmi_heatmaps_to_keypoints_workspace_bytes(R, K);
+  at::Tensor ws = at::empty({(int64_t)wb}, maps.options().dtype(at::kByte));
+  check_status(tvmi_heatmaps_to_keypoints(m.const_data_ptr(), r.const_data_ptr<float>(), xy.mutable_data_ptr<float>(),
+                                          scores.mutable_data_ptr<float>(), dtype_of(maps, "heatmaps_to_keypoints"), R, K, H,
+                                          W, ws.mutable_data_ptr(), wb, current_stream(maps)),
+               "heatmaps_to_keypoints");
+  return std::make_tuple(xy.permute({0, 2, 1}), scores);
+}
+
 // ---- candidate generation for the two post-processing stages (postprocess.hip)
 std::tuple<at::Tensor, at::Tensor, at::Tensor> detection_candidates(const at::Tensor& class_logits,
                                                                     const at::Tensor& box_regression,
@@ -1652,6 +1677,8 @@ TORCH_LIBRARY(tvmi, m) {
   m.def("boxes_to_rois(Tensor[] boxes) -> Tensor");
   // python loop of roi_heads.py:486-500 (pad + expand + resize + paste per detection) as one launch
   m.def("paste_masks(Tensor masks, Tensor boxes, int im_h, int im_w, int padding) -> Tensor");
+  // python loop of roi_heads.py heatmaps_to_keypoints (bicubic resize + argmax per detection) in three launches
+  m.def("heatmaps_to_keypoints(Tensor maps, Tensor rois) -> (Tensor, Tensor)");
   m.def(
       "interpolate2d(Tensor input, int out_h, int out_w, int mode, bool align_corners, bool antialias, float scale_h, float scale_w) -> Tensor");
   // its gradient, gathered (deterministic): grad_output [N,C,OH,OW] -> grad_input [N,C,in_h,in_w]
@@ -1689,6 +1716,7 @@ TORCH_LIBRARY_IMPL(tvmi, CUDA, m) {
   m.impl("multiscale_roi_align_backward", &multiscale_roi_align_backward);
   m.impl("pack_detections", &pack_detections);
   m.impl("paste_masks", &paste_masks);
+  m.impl("heatmaps_to_keypoints", &heatmaps_to_keypoints);
   m.impl("boxes_to_rois", &boxes_to_rois);
   m.impl("sort_scores_desc", &sort_scores_desc);
   m.impl("normalize_resize_batch", &normalize_resize_batch);

@@ -9,6 +9,7 @@ TVMI_NO_PY_REGISTRATIONS=1 if `vision_amd` is imported in the same process: the 
 package brings its own fake/autograd/autocast registrations for the same schemas.
 """
 import os
+import sys
 import types
 
 from . import _loader
@@ -187,7 +188,39 @@ def make_deterministic_roi_align(orig):
     return _roi_align
 
 
-def fuse_detection_model(model, paste_masks: bool = True, transform: bool = True):
+def make_keypointrcnn_inference(orig):
+    """The module-level `keypointrcnn_inference(x, boxes)` of roi_heads.py (-> heatmaps_to_keypoints, a per-detection loop
+    with two host syncs each) -> `vision_amd.keypointrcnn_inference`, one sync-free launch sequence for the batch.  Tracing /
+    scripting (the reference's ONNX branch), CPU tensors and dtypes other than float32 / float16 / bfloat16 run `orig`."""
+    import torch
+
+    from . import keypoints
+
+    def keypointrcnn_inference(x, boxes):
+        if (_tracing() or not x.is_cuda or not all(b.is_cuda for b in boxes)
+                or x.dtype not in (torch.float32, torch.float16, torch.bfloat16)):
+            return orig(x, boxes)
+        return keypoints.keypointrcnn_inference(x, boxes)
+    return keypointrcnn_inference
+
+
+def _swap_keypointrcnn_inference(module):
+    """Route the module global `keypointrcnn_inference` of `module` (the one RoIHeads.forward calls) to the fused function.
+    The wrapper carries `_tvmi_autofused`, so a second swap (by this function or by `vision_amd.autofuse`) is a no-op, and
+    `vision_amd.autofuse.uninstall()` puts the original back."""
+    from . import autofuse
+
+    orig = getattr(module, "keypointrcnn_inference", None)
+    if orig is None or getattr(orig, "_tvmi_autofused", False):
+        return
+    fn = make_keypointrcnn_inference(orig)
+    fn.__wrapped__ = orig
+    fn._tvmi_autofused = True
+    setattr(module, "keypointrcnn_inference", fn)
+    autofuse._patched.append((module, "keypointrcnn_inference", orig))
+
+
+def fuse_detection_model(model, paste_masks: bool = True, transform: bool = True, keypoints: bool = True):
     """Swap the fused `vision_amd` pieces into a detection model of the reference (`torchvision.models.detection`:
     Faster R-CNN / Mask R-CNN / Keypoint R-CNN = GeneralizedRCNN with RoIHeads + RPN, or RetinaNet), in place, and return it.
     The model keeps its weights, its python class and its output format; what changes is how the hot path runs:
@@ -199,10 +232,17 @@ def fuse_detection_model(model, paste_masks: bool = True, transform: bool = True
       RetinaNet.postprocess_detections   -> `vision_amd.retinanet_postprocess_detections` (retinanet.py:509-571)
       transform.forward (eval)           -> `vision_amd.transform_images`         (transform.py:119-255: one launch per batch)
       transform.postprocess              -> the reference's method with `vision_amd.paste_masks_in_image` (roi_heads.py:378-500)
+      keypointrcnn_inference             -> `vision_amd.keypointrcnn_inference`   (roi_heads.py heatmaps_to_keypoints: one sync-free
+                                                       launch sequence instead of a loop with two host syncs per detection)
 
-    Only attributes of THIS model are replaced (no module-level monkey patching; `vision_amd.autofuse` is the class-level,
-    opt-in form of the same swaps).  Every replaced method calls the reference's own when the fused path does not apply:
-    training mode / targets (targets are resized by the reference transform), CPU tensors, fixed_size / _skip_resize transforms.
+    Everything but keypoint inference replaces attributes of THIS model only (`vision_amd.autofuse` is the class-level, opt-in
+    form of the same swaps).  RoIHeads.forward calls `keypointrcnn_inference` as a module global, so for a model with a
+    `roi_heads.keypoint_predictor` (and keypoints=True) that global is swapped in the module of type(model.roi_heads), for
+    every caller in the process: the wrapper runs the reference's function for everything the fused op does not serve
+    (tracing / scripting, CPU tensors, other dtypes), it is marked `_tvmi_autofused` so it is installed once whether this
+    function or `vision_amd.autofuse` gets there first, and `vision_amd.autofuse.uninstall()` restores the original.
+    Every replaced method calls the reference's own when the fused path does not apply: training mode / targets (targets are
+    resized by the reference transform), CPU tensors, fixed_size / _skip_resize transforms.
     RetinaNet only: FCOS (fcos.py:426,489) and SSD / SSDlite (ssd.py:240,414) carry the same `topk_candidates` /
     `postprocess_detections` attributes but score with sqrt(cls * centerness) + BoxLinearCoder resp. softmax over one logits
     tensor — they keep the reference's post-processing.  Duck-typed: nothing of the reference package is imported."""
@@ -226,6 +266,10 @@ def fuse_detection_model(model, paste_masks: bool = True, transform: bool = True
             swap_pool(rh, name)
         if hasattr(rh, "box_coder") and hasattr(rh, "detections_per_img"):
             bind(rh, "postprocess_detections", make_postprocess_detections)
+        if keypoints and getattr(rh, "keypoint_predictor", None) is not None:
+            mod = sys.modules.get(type(rh).__module__)
+            if mod is not None:
+                _swap_keypointrcnn_inference(mod)
     if rpn is not None and hasattr(rpn, "pre_nms_top_n"):
         bind(rpn, "filter_proposals", make_filter_proposals)
     if rh is None and _is_retinanet(model):
