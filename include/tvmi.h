@@ -606,6 +606,29 @@ size_t tvmi_heatmaps_to_keypoints_workspace_bytes(int64_t R, int64_t K);
 int tvmi_heatmaps_to_keypoints(const void* maps, const float* rois, float* xy, float* scores, tvmi_dtype dt, int64_t R,
                                int64_t K, int64_t H, int64_t W, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------- ground-truth matching ---
+ * Batched replacement of box_iou(gt, boxes) + Matcher (models/detection/_utils.py) as called per image by
+ * RegionProposalNetwork.assign_targets_to_anchors, RoIHeads.assign_targets_to_proposals and RetinaNet.compute_loss: for every
+ * image b, the boxes [box_offsets[b], box_offsets[b+1]) are matched to the gt [gt_offsets[b], gt_offsets[b+1]).  The
+ * reference loops over images in Python with one host sync each; this is a workspace clear and at most two launches for
+ * the whole batch, sync-free.
+ *   boxes [N,4], gt [M,4] (dt: F32 only, xyxy, 16-byte aligned); box_offsets, gt_offsets [B+1] device int64, non-decreasing,
+ *   from 0 to N resp. M; gt_labels [M] int64 or NULL (then labels must be NULL too).
+ *   matches [N] int64: the Matcher's output, the image-local gt index of the first IoU argmax, -1 below `low`, -2 in
+ *   [low, high) (thresholds compared in float32; a NaN IoU keeps its index); with allow_low_quality, a box whose IoU with
+ *   some gt g equals g's best IoU gets back its own argmax.  An image without gt gets -1 everywhere.
+ *   matched_gt [N,4] float32: gt[clamp(matches, 0)], zeros for an image without gt;
+ *   labels [N] int64: gt_labels[clamp(matches, 0)], 0 for -1, -1 for -2 (RoIHeads' convention).
+ *   IoU values are bit-identical to box_iou; ties go to the lowest gt index; results are reproducible.
+ *   workspace: 256-byte aligned device scratch of at least tvmi_match_boxes_workspace_bytes(M) bytes (allow_low_quality only).
+ * Limits: N, M, B < 2^31 - 1, low <= high.  An image with gt but no boxes is the caller's error (the reference raises);
+ * N == 0 launches nothing. */
+size_t tvmi_match_boxes_workspace_bytes(int64_t M);
+int tvmi_match_boxes(const float* boxes, const int64_t* box_offsets, const float* gt, const int64_t* gt_offsets,
+                     const int64_t* gt_labels, tvmi_dtype dt, int64_t N, int64_t M, int64_t B, double high, double low,
+                     int allow_low_quality, int64_t* matches, float* matched_gt, int64_t* labels, void* workspace,
+                     size_t workspace_bytes, void* stream);
+
 /* ------------------------------------------------------------------ quantized ------
  * torchvision::qroi_align (quantized/cpu/qroi_align_kernel.cpp:22-178, CPU-only in the reference): `input` [1, C, H, W] and
  * `rois` [K, 5] are integer tensors of type `dt` with explicit (scale, zero point); bilinear sums on the raw integers,

@@ -66,6 +66,7 @@ from .poolers import LevelMapper, MultiScaleRoIAlign  # noqa: E402,F401
 from .resize import interpolate, resize  # noqa: E402,F401
 from .masks import expand_boxes, expand_masks, paste_masks_in_image  # noqa: E402,F401
 from .keypoints import heatmaps_to_keypoints, keypointrcnn_inference  # noqa: E402,F401
+from .matcher import match_boxes, roi_heads_assign_targets, rpn_assign_targets  # noqa: E402,F401
 from .detection_post import filter_proposals, postprocess_detections, retinanet_postprocess_detections  # noqa: E402,F401
 from .integration import fuse_detection_model  # noqa: E402,F401
 from .transform import resize_boxes, resize_keypoints, resized_size, transform_images  # noqa: E402,F401

@@ -196,6 +196,12 @@ def _fake_heatmaps_to_keypoints(maps, rois):
     return xy, maps.new_empty((R, K), dtype=torch.float32)
 
 
+def _fake_match_boxes(boxes, box_offsets, gt, gt_offsets, gt_labels, high, low, allow_low_quality):
+    N = boxes.shape[0]
+    return (boxes.new_empty((N,), dtype=torch.int64), boxes.new_empty((N, 4)),
+            boxes.new_empty((N if gt_labels is not None else 0,), dtype=torch.int64))
+
+
 def _fake_detection_candidates(class_logits, box_regression, proposals, row_image, image_hw, weights, clip, score_thresh, min_size):
     R, C = class_logits.shape
     f = class_logits.new_empty
@@ -282,6 +288,7 @@ _FAKES = {
     "tvmi::pack_detections_devcount": _fake_pack_devcount,
     "tvmi::paste_masks": _fake_paste_masks,
     "tvmi::heatmaps_to_keypoints": _fake_heatmaps_to_keypoints,
+    "tvmi::match_boxes": _fake_match_boxes,
     "tvmi::detection_candidates": _fake_detection_candidates,
     "tvmi::rpn_candidates": _fake_rpn_candidates,
     "tvmi::pack_detections": _fake_pack_detections,

@@ -1158,6 +1158,46 @@ std::tuple<at::Tensor, at::Tensor> heatmaps_to_keypoints(const at::Tensor& maps,
   return std::make_tuple(xy.permute({0, 2, 1}), scores);
 }
 
+// ---- batched box_iou + Matcher of detector training (rpn.py / roi_heads.py / retinanet.py) in <= 2 launches, no host sync
+std::tuple<at::Tensor, at::Tensor, at::Tensor> match_boxes(const at::Tensor& boxes, const at::Tensor& box_offsets,
+                                                           const at::Tensor& gt, const at::Tensor& gt_offsets,
+                                                           const c10::optional<at::Tensor>& gt_labels, double high, double low,
+                                                           bool allow_low_quality) {
+  TORCH_CHECK(boxes.is_cuda() && gt.is_cuda() && box_offsets.is_cuda() && gt_offsets.is_cuda(),
+              "match_boxes: CUDA tensors expected");
+  TORCH_CHECK(boxes.dim() == 2 && boxes.size(1) == 4 && gt.dim() == 2 && gt.size(1) == 4,
+              "match_boxes: boxes and gt must have shape [N, 4] and [M, 4]");
+  TORCH_CHECK(boxes.scalar_type() == at::kFloat && gt.scalar_type() == at::kFloat, "match_boxes: float32 boxes expected");
+  TORCH_CHECK(box_offsets.dim() == 1 && box_offsets.size(0) >= 1 && box_offsets.scalar_type() == at::kLong &&
+                  gt_offsets.sizes() == box_offsets.sizes() && gt_offsets.scalar_type() == at::kLong,
+              "match_boxes: box_offsets and gt_offsets must be int64 [B + 1]");
+  TORCH_CHECK(low <= high, "match_boxes: low threshold above high threshold");
+  const bool with_labels = gt_labels.has_value() && gt_labels->defined();
+  if (with_labels)
+    TORCH_CHECK(gt_labels->is_cuda() && gt_labels->dim() == 1 && gt_labels->size(0) == gt.size(0) &&
+                    gt_labels->scalar_type() == at::kLong,
+                "match_boxes: gt_labels must be int64 [M]");
+  c10::DeviceGuard guard(boxes.device());
+  const int64_t N = boxes.size(0), M = gt.size(0), B = box_offsets.size(0) - 1;
+  at::Tensor matches = at::empty({N}, boxes.options().dtype(at::kLong));
+  at::Tensor matched = at::empty({N, 4}, boxes.options());
+  at::Tensor labels = at::empty({with_labels ? N : 0}, boxes.options().dtype(at::kLong));
+  if (N == 0) return std::make_tuple(matches, matched, labels);
+  at::Tensor b = boxes.contiguous(), g = gt.contiguous(), bo = box_offsets.contiguous(), go = gt_offsets.contiguous();
+  if ((uintptr_t)b.const_data_ptr() & 15) b = b.clone();  // the kernels read float4 rows
+  if ((uintptr_t)g.const_data_ptr() & 15) g = g.clone();
+  at::Tensor gl = with_labels ? gt_labels->contiguous() : at::Tensor();
+  const size_t wb = allow_low_quality ? tvmi_match_boxes_workspace_bytes(M) : 0;
+  at::Tensor ws = at::empty({(int64_t)wb}, boxes.options().dtype(at::kByte));
+  check_status(tvmi_match_boxes(b.const_data_ptr<float>(), bo.const_data_ptr<int64_t>(), M ? g.const_data_ptr<float>() : nullptr,
+                                go.const_data_ptr<int64_t>(), with_labels ? gl.const_data_ptr<int64_t>() : nullptr, TVMI_F32, N,
+                                M, B, high, low, allow_low_quality ? 1 : 0, matches.mutable_data_ptr<int64_t>(),
+                                matched.mutable_data_ptr<float>(), with_labels ? labels.mutable_data_ptr<int64_t>() : nullptr,
+                                wb ? ws.mutable_data_ptr() : nullptr, wb, current_stream(boxes)),
+               "match_boxes");
+  return std::make_tuple(matches, matched, labels);
+}
+
 // ---- candidate generation for the two post-processing stages (postprocess.hip)
 std::tuple<at::Tensor, at::Tensor, at::Tensor> detection_candidates(const at::Tensor& class_logits,
                                                                     const at::Tensor& box_regression,
@@ -1679,6 +1719,9 @@ TORCH_LIBRARY(tvmi, m) {
   m.def("paste_masks(Tensor masks, Tensor boxes, int im_h, int im_w, int padding) -> Tensor");
   // python loop of roi_heads.py heatmaps_to_keypoints (bicubic resize + argmax per detection) in three launches
   m.def("heatmaps_to_keypoints(Tensor maps, Tensor rois) -> (Tensor, Tensor)");
+  // python loop of box_iou + Matcher per image (rpn.py / roi_heads.py / retinanet.py training targets) in <= 2 launches
+  m.def(
+      "match_boxes(Tensor boxes, Tensor box_offsets, Tensor gt, Tensor gt_offsets, Tensor? gt_labels, float high, float low, bool allow_low_quality) -> (Tensor, Tensor, Tensor)");
   m.def(
       "interpolate2d(Tensor input, int out_h, int out_w, int mode, bool align_corners, bool antialias, float scale_h, float scale_w) -> Tensor");
   // its gradient, gathered (deterministic): grad_output [N,C,OH,OW] -> grad_input [N,C,in_h,in_w]
@@ -1717,6 +1760,7 @@ TORCH_LIBRARY_IMPL(tvmi, CUDA, m) {
   m.impl("pack_detections", &pack_detections);
   m.impl("paste_masks", &paste_masks);
   m.impl("heatmaps_to_keypoints", &heatmaps_to_keypoints);
+  m.impl("match_boxes", &match_boxes);
   m.impl("boxes_to_rois", &boxes_to_rois);
   m.impl("sort_scores_desc", &sort_scores_desc);
   m.impl("normalize_resize_batch", &normalize_resize_batch);

@@ -220,7 +220,85 @@ def _swap_keypointrcnn_inference(module):
     autofuse._patched.append((module, "keypointrcnn_inference", orig))
 
 
-def fuse_detection_model(model, paste_masks: bool = True, transform: bool = True, keypoints: bool = True):
+# ---- training targets (opt-in: fuse_detection_model(..., training_targets=True)).  The reference's sampler
+# (BalancedPositiveNegativeSampler) and BoxCoder.encode stay as they are, so a fused step draws the same samples.
+def _is_reference_matcher(m) -> bool:
+    """The reference's det_utils.Matcher (models/detection/_utils.py), by class name and attributes; a subclass (SSDMatcher)
+    or any other matcher is not."""
+    return (type(m).__name__ == "Matcher" and all(hasattr(m, a) for a in ("high_threshold", "low_threshold",
+                                                                          "allow_low_quality_matches"))
+            and getattr(m, "BELOW_LOW_THRESHOLD", None) == -1 and getattr(m, "BETWEEN_THRESHOLDS", None) == -2)
+
+
+def _is_reference_box_iou(fn) -> bool:
+    """ops/boxes.py box_iou, the similarity the fused kernel restates bit for bit."""
+    return getattr(fn, "__name__", None) == "box_iou" and getattr(fn, "__module__", None) == "torchvision.ops.boxes"
+
+
+def _fp32_cuda(ts) -> bool:
+    import torch
+
+    return all(t.is_cuda and t.dtype == torch.float32 for t in ts)
+
+
+def _defined_by(obj, method: str, class_name: str) -> bool:
+    """`method` of type(obj) is the one class `class_name` defines (a subclass that overrides it keeps its own)."""
+    for c in type(obj).__mro__:
+        if method in c.__dict__:
+            return c.__name__ == class_name
+    return False
+
+
+def make_assign_targets_to_anchors(orig):
+    """RegionProposalNetwork.assign_targets_to_anchors (rpn.py): box_iou + Matcher per image (one host sync each) ->
+    `vision_amd.rpn_assign_targets`, one sync-free launch sequence for the batch.  Tracing / scripting, CPU or non-float32
+    boxes, a box_similarity other than box_iou and a matcher other than the reference's Matcher run `orig`."""
+    from . import matcher
+
+    def assign_targets_to_anchors(self, anchors, targets):
+        m = self.proposal_matcher
+        if (_tracing() or not len(anchors) or not _is_reference_matcher(m) or not _is_reference_box_iou(self.box_similarity)
+                or not _fp32_cuda(list(anchors) + [t["boxes"] for t in targets])):
+            return orig(self, anchors, targets)
+        return matcher.rpn_assign_targets(anchors, targets, m.high_threshold, m.low_threshold, m.allow_low_quality_matches)
+    return assign_targets_to_anchors
+
+
+def make_assign_targets_to_proposals(orig):
+    """RoIHeads.assign_targets_to_proposals (roi_heads.py): box_iou + Matcher per image -> `vision_amd.roi_heads_assign_targets`
+    (the reference calls box_ops.box_iou here, not self.box_similarity).  Tracing / scripting, CPU or non-float32 boxes and a
+    matcher other than the reference's Matcher run `orig`."""
+    from . import matcher
+
+    def assign_targets_to_proposals(self, proposals, gt_boxes, gt_labels):
+        m = self.proposal_matcher
+        if (_tracing() or not len(proposals) or not _is_reference_matcher(m)
+                or not _fp32_cuda(list(proposals) + list(gt_boxes)) or not all(lb.is_cuda for lb in gt_labels)):
+            return orig(self, proposals, gt_boxes, gt_labels)
+        return matcher.roi_heads_assign_targets(proposals, gt_boxes, gt_labels, m.high_threshold, m.low_threshold,
+                                                m.allow_low_quality_matches)
+    return assign_targets_to_proposals
+
+
+def make_retinanet_compute_loss(orig):
+    """RetinaNet.compute_loss (retinanet.py): the per-image box_iou + Matcher of `matched_idxs` -> `vision_amd.match_boxes`
+    for the batch, then the model's own `self.head.compute_loss`.  Tracing / scripting, CPU or non-float32 boxes and a
+    matcher other than the reference's Matcher run `orig`."""
+    from . import matcher
+
+    def compute_loss(self, targets, head_outputs, anchors):
+        m = self.proposal_matcher
+        if (_tracing() or not len(anchors) or not _is_reference_matcher(m)
+                or not _fp32_cuda(list(anchors) + [t["boxes"] for t in targets])):
+            return orig(self, targets, head_outputs, anchors)
+        matched_idxs = matcher.match_boxes([t["boxes"] for t in targets], anchors, m.high_threshold, m.low_threshold,
+                                           m.allow_low_quality_matches)
+        return self.head.compute_loss(targets, head_outputs, anchors, matched_idxs)
+    return compute_loss
+
+
+def fuse_detection_model(model, paste_masks: bool = True, transform: bool = True, keypoints: bool = True,
+                         training_targets: bool = False):
     """Swap the fused `vision_amd` pieces into a detection model of the reference (`torchvision.models.detection`:
     Faster R-CNN / Mask R-CNN / Keypoint R-CNN = GeneralizedRCNN with RoIHeads + RPN, or RetinaNet), in place, and return it.
     The model keeps its weights, its python class and its output format; what changes is how the hot path runs:
@@ -234,6 +312,13 @@ def fuse_detection_model(model, paste_masks: bool = True, transform: bool = True
       transform.postprocess              -> the reference's method with `vision_amd.paste_masks_in_image` (roi_heads.py:378-500)
       keypointrcnn_inference             -> `vision_amd.keypointrcnn_inference`   (roi_heads.py heatmaps_to_keypoints: one sync-free
                                                        launch sequence instead of a loop with two host syncs per detection)
+
+    With training_targets=True (off by default) the ground-truth matching of a training step is swapped too, on this model:
+      rpn.assign_targets_to_anchors      -> `vision_amd.rpn_assign_targets`       (rpn.py: box_iou + Matcher per image)
+      roi_heads.assign_targets_to_proposals -> `vision_amd.roi_heads_assign_targets` (roi_heads.py)
+      RetinaNet.compute_loss             -> `vision_amd.match_boxes`, then the model's own head.compute_loss (retinanet.py)
+    each only where the reference's class defines the method; tracing / scripting, CPU or non-float32 boxes, a box_similarity
+    other than box_iou (RPN) and a matcher other than the reference's Matcher run the reference's method.
 
     Everything but keypoint inference replaces attributes of THIS model only (`vision_amd.autofuse` is the class-level, opt-in
     form of the same swaps).  RoIHeads.forward calls `keypointrcnn_inference` as a module global, so for a model with a
@@ -274,6 +359,13 @@ def fuse_detection_model(model, paste_masks: bool = True, transform: bool = True
         bind(rpn, "filter_proposals", make_filter_proposals)
     if rh is None and _is_retinanet(model):
         bind(model, "postprocess_detections", make_retinanet_postprocess)
+    if training_targets:
+        if rpn is not None and _defined_by(rpn, "assign_targets_to_anchors", "RegionProposalNetwork"):
+            bind(rpn, "assign_targets_to_anchors", make_assign_targets_to_anchors)
+        if rh is not None and _defined_by(rh, "assign_targets_to_proposals", "RoIHeads"):
+            bind(rh, "assign_targets_to_proposals", make_assign_targets_to_proposals)
+        if rh is None and _defined_by(model, "compute_loss", "RetinaNet"):
+            bind(model, "compute_loss", make_retinanet_compute_loss)
     tr = getattr(model, "transform", None)
     if tr is not None and transform and hasattr(tr, "image_mean"):
         bind(tr, "forward", make_transform_forward)
